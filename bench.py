@@ -14,10 +14,21 @@ shared files and decodes them on its own GPU.  `--gpus N` with no WORLD_SIZE in 
 environment launches the N ranks itself (torch.distributed.run, before touching the GPU).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload c2|c2nori|c3|c4|c5]
+                    [--dump-outputs DIR] [--full]
 
-At N = 1 the line also carries `extra_workloads`: the other BASELINE configs measured in the
-same run with the same contract -- c2nori (the no-DRI twin set), C3 (4:4:4 +
-4:2:2 -> YUV_PLANAR), C4 (mixed resolution, per GPU) and C5 (progressive).
+A plain run does only what the headline figure needs: it generates (or finds) the dataset, makes
+the streams resident, lets the handle finish its once-only entry-placement search, runs W warm-up
+steps, times one run of exactly K steps and prints the result line (`value`, `ms_per_step`).
+`--dump-outputs DIR` then writes what the last timed step decoded (a fixed, seeded sample of the
+destination bytes) as DIR/<name>.npy, so that two builds can be compared output for output: with
+the same arguments the inputs are identical from run to run.
+
+`--full` adds everything else to the line: the median of `--runs` (5) timed runs, the parity of
+the timed output against the CPU oracle, the profiled pass (roofline, per-stage and per-kernel
+times), the host-input and parse rates, the reference's call shapes, the CPU baselines, and at
+N = 1 `extra_workloads`: the other BASELINE configs measured in the same run with the same
+contract -- c2nori (the no-DRI twin set), C3 (4:4:4 + 4:2:2 -> YUV_PLANAR), C4
+(mixed resolution, per GPU) and C5 (progressive).
 """
 import argparse
 import ctypes
@@ -43,6 +54,7 @@ PROG_KERNELS = ("k_prog", "k_prog_wave", "k_prog_fold")  # RocJpegAmdTimings.pro
 C4_SIZES = [(640, 480), (1280, 720), (1920, 1080), (2560, 1440), (3840, 2160)]
 SEED0 = 1234
 GEN_VERSION = 1  # bump when the generator changes (dataset files are cached per node)
+DUMP_ELEMS = 12 << 20  # --dump-outputs: float32 values over all ranks (48 MB)
 
 # generator arguments: (w, h, subsampling, restart = one MCU row, progressive); w == 0: C4 sizes
 # by seed; sub == -1: 4:4:4 / 4:2:2 alternating by seed (C3)
@@ -245,7 +257,7 @@ class BatchRun:
     destinations in one HBM arena sized as the reference samples size them
     (samples/rocjpeg_samples_utils.h:318-399, tests/gpu_util.py channel_shapes)."""
 
-    def __init__(self, dec, datas, fmt, dev):
+    def __init__(self, dec, datas, fmt, dev, parse_rate=True):
         import torch
         import rocjpeg_amd as R
         from tests.gpu_util import channel_shapes
@@ -258,7 +270,7 @@ class BatchRun:
         # reported is the median of 3 further calls on the same images (their streams closed)
         self.parse_first_s = time.perf_counter() - t0
         warm = []
-        for _ in range(3):
+        for _ in range(3 if parse_rate else 0):
             t0 = time.perf_counter()
             st, extra = dec.parse_device(datas)
             warm.append(time.perf_counter() - t0)
@@ -267,7 +279,7 @@ class BatchRun:
                 x.close()
             if st != 0:
                 raise RuntimeError(f"rocJpegAmdStreamParseDevice: {R.error_name(st)}")
-        self.parse_s = float(np.median(warm))
+        self.parse_s = float(np.median(warm)) if warm else self.parse_first_s
         dec.streams_to_device(self.streams)  # progressive streams are host-parsed: make them resident too
         self.shapes = []
         for s in self.streams:
@@ -294,6 +306,30 @@ class BatchRun:
         st = self.R.lib().rocJpegDecodeBatched(self.dec.handle, self.hs, self.n, ctypes.byref(self.params), self.arr)
         if st != 0:
             raise RuntimeError(self.R.error_name(st))
+
+    def settle(self, calls=5):
+        """A handle tries three entry buffers on its first large calls (two to warm up, one per
+        candidate: rj_decoder.h) and keeps the fastest.  These untimed calls let that once-only
+        search finish, so that the warm-up and the timed steps of a single run all see the
+        steady state, as the median of several runs does."""
+        for _ in range(calls):
+            self.step()
+
+    def dump(self, dirpath, name, limit):
+        """What the last step wrote, as a caller receives it: the bytes of this rank's
+        destination arena (every image's channels back to back) as float32 -- all of them when
+        they fit in `limit` values, else the values at `limit` seeded positions (the same
+        positions in every run of the same arguments)."""
+        import torch
+        torch.cuda.synchronize()
+        total = self.out.numel() if self.n else 0
+        if total <= limit:
+            got = self.out[:total]
+        else:
+            idx = np.random.default_rng(SEED0).integers(0, total, limit)
+            got = self.out[torch.from_numpy(idx).to(self.out.device)]
+        os.makedirs(dirpath, exist_ok=True)
+        np.save(os.path.join(dirpath, name + ".npy"), got.cpu().numpy().astype(np.float32))
 
     def timed(self, steps, warmup, world=1, dev=None):  # dev: where the collective's tensors live
         """W untimed steps, then K steps bracketed by barrier + synchronize; max over ranks."""
@@ -712,13 +748,22 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--runs", type=int, default=5, help="timed runs of K steps; value = the median run (SURVEY 8d)")
+    ap.add_argument("--runs", type=int, default=None,
+                    help="timed runs of K steps; value = the median run (SURVEY 8d); default 1, with --full 5")
+    ap.add_argument("--full", action="store_true",
+                    help="also: parity, roofline and per-kernel times, host-input and parse rates, call shapes, "
+                         "the other BASELINE configs, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step decoded (a seeded sample, float32) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=1024, help="images per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the other BASELINE configs at N=1")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the other BASELINE configs and the call shapes at N=1")
     ap.add_argument("--path", type=int, default=0, help="0 auto (fused where legal), 1 general two-stage path")
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     args = ap.parse_args()
+    if args.runs is None:
+        args.runs = 5 if args.full else 1
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # one process per GPU, launched before this process touches the GPU; exit with its code
@@ -735,7 +780,8 @@ def main():
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
         sys.exit(2)
     wl = WORKLOADS[args.workload]
-    extras = [] if (world > 1 or args.no_extras) else [w for w in ("c2nori", "c3", "c4", "c5") if w != args.workload]
+    extras = ([] if (world > 1 or args.no_extras or not args.full)
+              else [w for w in ("c2nori", "c3", "c4", "c5") if w != args.workload])
 
     # ---- host only (no GPU call yet): this rank's dataset part, the extra configs' data,
     # the CPU baseline's processes ----
@@ -748,7 +794,7 @@ def main():
     gen_pool.join()
     t_gen = time.perf_counter() - t_gen
     turbo = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # the CPU comparator: N = 1 only
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:  # the CPU comparator: N = 1 only
         turbo = TurboBaseline(mine[0], mine[1], mine[2], cores)
 
     import torch
@@ -777,15 +823,17 @@ def main():
     fmt = getattr(R.OutputFormat, wl["fmt"])
     t_tab = time.perf_counter()
     shard_cost, bcast_via = None, "none (one rank)"
+    table, t_build = None, 0.0
     if world == 1:
         # N = 1: the drop-in call itself, rocJpegDecodeBatched over resident streams
         raw = np.memmap(mine[0], dtype=np.uint8, mode="r")
         datas = [bytes(raw[int(o):int(o) + int(z)]) for o, z in zip(mine[1], mine[2])]
-        table = S.build_work_table(raw, mine[1], mine[2])
+        if args.full:  # the work table is only reported at one rank
+            table = S.build_work_table(raw, mine[1], mine[2])
+            shard_cost = S.assign_shards(table, 1)
         del raw
-        shard_cost = S.assign_shards(table, 1)
         t_build = t_tab = time.perf_counter() - t_tab
-        run = BatchRun(dec, datas, fmt, dev)
+        run = BatchRun(dec, datas, fmt, dev, parse_rate=args.full)
     else:
         # N > 1: the C-ABI sharded entry a C caller uses (include/rocjpeg_amd.h): the batch is one
         # blob on the node (the ranks' parts concatenated), rocJpegAmdShardCreate plans on rank 0,
@@ -814,16 +862,79 @@ def main():
     datas = run.datas
     n = run.n
 
-    # the median of >= 5 timed runs, each exactly K steps bracketed by barrier +
-    # synchronize (max over ranks); the warm-up steps precede the first run only
+    # a plain run: one timed run of exactly K steps bracketed by barrier + synchronize (max over
+    # ranks), after the handle's placement search and the warm-up steps.  --full, SURVEY.md 8(d):
+    # the median of >= 5 such runs; the warm-up steps precede the first run only
+    if not args.full:
+        run.settle()
     runs = [run.timed(args.steps, args.warmup if r == 0 else 0, world, cdev) for r in range(max(1, args.runs))]
     elapsed = float(np.median(runs))
-    # parity of the timed run's own output (the last step's), before anything else writes it
-    parity = run.parity(parity_sample(n))
+    # the timed run's own output (the last step's), before anything else writes it
+    if args.dump_outputs:
+        run.dump(args.dump_outputs, "decoded" if world == 1 else f"decoded_rank{rank}", DUMP_ELEMS // world)
     imgs = torch.tensor([n], dtype=torch.int64, device=cdev)
     if world > 1:
         dist.all_reduce(imgs)
     imgs_total = int(imgs.item()) * args.steps
+
+    res = None
+    if rank == 0:
+        K = args.steps
+        res = {
+            "metric": "images/s (1080p 4:2:0 batch) at 1/2/4/8 MI355X + achieved HBM GB/s",
+            "value": round(imgs_total / elapsed, 2),
+            "unit": "images/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / K * 1e3, 4),
+            "runs": {"count": len(runs), "statistic": "median",
+                     "ms_per_step": [round(x / K * 1e3, 4) for x in runs],
+                     "spread": round((max(runs) - min(runs)) / elapsed, 5)},
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": wl["data"],
+            "config": {"workload": wl["workload"].format(batch=args.batch), "batch_per_gpu": args.batch,
+                       "output_format": wl["fmt"],
+                       "parallelism": f"images sharded over {world} rank(s) by LPT on a broadcast work table"},
+            **({"rehearsal": "RJ_BENCH_SHARE_GPU: ranks share the visible GPUs over gloo, not a scaling measurement"}
+               if share and world > 1 else {}),
+            "dataset_gen_s": round(t_gen, 1),
+        }
+    if args.full:
+        full_details(args, res, run, dec, fmt, dev, rank, world, imgs_total, elapsed, table, t_build, bcast_via,
+                     shard_cost)
+    run.close()
+    if rank == 0 and extras:
+        res["extra_workloads"] = {w: run_extra(w, dec, extra_data[w], max(3, args.steps // 2), 1, dev) for w in extras}
+    if rank == 0:
+        if turbo is not None:
+            rate, nimg, wall = turbo.run()
+            res["cpu_baseline"] = {
+                "value": round(rate, 1), "unit": "images/s", "cores": cores, "kind": "reference",
+                "lib": "libjpeg-turbo 3.1 (Pillow bundle): the reference's host decode path of BASELINE config C1; "
+                       "BT.601 + fancy upsampling, a throughput comparator, not a parity oracle",
+                "sample": f"{nimg} decodes of this run's images, {cores} processes (one per core; {core_rule}; "
+                          f"nproc={nproc}), ~{wall:.1f} s each, per-process rates summed as jpegdecodeperf.cpp does"}
+            res["cpu_oracle_1core"] = cpu_oracle(datas, run.shapes, int(fmt))
+        print(json.dumps(res), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_details(args, res, run, dec, fmt, dev, rank, world, imgs_total, elapsed, table, t_build, bcast_via,
+                 shard_cost):
+    """--full: everything about the main workload beyond the headline figure, measured after the
+    timed runs on the same handle and batch (every rank runs the passes; rank 0 adds them to `res`)."""
+    import torch
+    import rocjpeg_amd as R
+    from rocjpeg_amd import shard as S
+    datas, n = run.datas, run.n
+    # parity of the timed run's own output (the last step's), before anything else writes it
+    parity = run.parity(parity_sample(n))
 
     t = run.profiled(max(2, min(args.steps, 5)))
     per_img = (t["ecs_bytes"] + TABLE_BYTES * n + t["output_bytes"]) / n
@@ -854,31 +965,9 @@ def main():
         except Exception as e:  # reported in the line, never silent
             shapes_res = {"error": repr(e)}
 
-    res = None
     if rank == 0:
-        K = args.steps
-        res = {
-            "metric": "images/s (1080p 4:2:0 batch) at 1/2/4/8 MI355X + achieved HBM GB/s",
-            "value": round(imgs_total / elapsed, 2),
-            "unit": "images/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / K * 1e3, 4),
-            "runs": {"count": len(runs), "statistic": "median",
-                     "ms_per_step": [round(x / K * 1e3, 4) for x in runs],
-                     "spread": round((max(runs) - min(runs)) / elapsed, 5)},
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": wl["data"],
-            "config": {"workload": wl["workload"].format(batch=args.batch), "batch_per_gpu": args.batch,
-                       "output_format": wl["fmt"],
-                       "parallelism": f"images sharded over {world} rank(s) by LPT on a broadcast work table",
-                       "ecs_bytes_per_image": round(t["ecs_bytes"] / n)},
-            **({"rehearsal": "RJ_BENCH_SHARE_GPU: ranks share the visible GPUs over gloo, not a scaling measurement"}
-               if share and world > 1 else {}),
+        res["config"]["ecs_bytes_per_image"] = round(t["ecs_bytes"] / n)
+        res.update({
             "roofline": rf,
             "stages_ms_per_step": {k: round(t[k], 4) for k in ("host_ms", "h2d_ms", "destuff_ms", "huffman_ms",
                                                                 "idct_ms", "output_ms", "total_ms")},
@@ -905,31 +994,13 @@ def main():
                            "broadcast": bcast_via,
                            "lpt_imbalance": round(S.imbalance(shard_cost), 5),
                            "images_per_rank": [int((table["shard"] == r).sum()) for r in range(world)]},
-            "dataset_gen_s": round(t_gen, 1),
-        }
+        })
         if shapes_res is not None:
             res["call_shapes"] = shapes_res
         if t["prog_images"]:
             res["progressive_detail"] = {"images": t["prog_images"], "intervals": t["prog_intervals"],
                                          "levels": t["prog_levels"], "k1p_ms": round(t["prog_entropy_ms"], 4),
                                          "k2_dense_ms": round(t["prog_rows_ms"], 4)}
-    run.close()
-    if rank == 0 and extras:
-        res["extra_workloads"] = {w: run_extra(w, dec, extra_data[w], max(3, args.steps // 2), 1, dev) for w in extras}
-    if rank == 0:
-        if turbo is not None:
-            rate, nimg, wall = turbo.run()
-            res["cpu_baseline"] = {
-                "value": round(rate, 1), "unit": "images/s", "cores": cores, "kind": "reference",
-                "lib": "libjpeg-turbo 3.1 (Pillow bundle): the reference's host decode path of BASELINE config C1; "
-                       "BT.601 + fancy upsampling, a throughput comparator, not a parity oracle",
-                "sample": f"{nimg} decodes of this run's images, {cores} processes (one per core; {core_rule}; "
-                          f"nproc={nproc}), ~{wall:.1f} s each, per-process rates summed as jpegdecodeperf.cpp does"}
-            res["cpu_oracle_1core"] = cpu_oracle(datas, run.shapes, int(fmt))
-        print(json.dumps(res), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""Print the headline numbers of a bench.py JSON line (file argument: a log holding the line)."""
+"""Print the headline numbers of a `bench.py --full` JSON line (file argument: a log holding the line)."""
 import json
 import sys
 

@@ -8,7 +8,7 @@ largest grid and the dispatches up to the next k_destuff; DecodeSplit's part cal
 dispatches of each kernel are summed: k_entropy = the chunk/exact pass (k_entropy<false, *>), k_rows = both
 K2 variants.  Writes profiles/pmc_traffic.json for bench.py's roofline.traffic.
 
-    python3 tools/pmc_traffic.py gpurun_out/pmc_<tag> <batch> [out.json]
+    python3 tools/pmc_traffic.py $RJ_OUT/pmc_<tag> <batch> [out.json]
 """
 import collections
 import csv
